@@ -18,6 +18,10 @@ the spare HBM keeps gathered parameters resident across micro-batches
 `--pipe P` switches to BASELINE config 4 (PipelineModule PP=P x DP=N/P, ZeRO-1 or 1-bit
 Adam via `--optimizer onebitadam`).
 
+A plain run sets up, warms up, times the K steps and prints the result line; `--dump-outputs DIR`
+also writes the last timed step's loss and a seeded sample of the parameters it left as .npy
+files, and `--full` is where anything beyond the headline figure goes (nothing yet).
+
 Rank 0 prints ONE JSON line.  `vs_baseline` divides by the only DeeperSpeed-derived
 number BASELINE.md gives for this model/metric (410 tokens/s per GPU: the reference's best
 published ZeRO-3 efficiency of 49 TFLOPS/GPU applied to 20B at 6N FLOPs/token), times N.
@@ -146,7 +150,51 @@ def parse():
                         "for N >= 2 -- the emulated N = 2 / 4 / 8 ranks measured -2.3 / -2.1 / +0.1 %% per-rank "
                         "throughput and 33.5 vs 22.3 GB/s of xGMI at N = 8 (profiles/r6a_emulated_world_notes.md); "
                         "one rank reduces nothing")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                        "(float32): loss.npy, the loss that step returned, and params_sample.npy, a fixed seeded "
+                        "sample of the parameters it left behind (see dump_outputs).  Weights and token batches "
+                        "are seeded, so two builds run with the same arguments can be compared output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run what is not needed for the headline figure.  A plain run already does only "
+                        "setup, warmup, the timed steps and the result line: every other measurement of this "
+                        "script is an opt-in flag of its own (--profile-steps, --memtrace, --emulate-world), so "
+                        "--full adds nothing yet; further baselines, sweeps or reference comparisons belong "
+                        "behind it")
     return p.parse_args()
+
+
+DUMP_SEED = 20240607
+DUMP_PER_PARAM = 4096  # sampled elements per parameter tensor (GPT-NeoX-20B: 532 tensors, 8.7 MB of float32)
+
+
+def dump_outputs(path, loss, module):
+    """--dump-outputs: what a caller of the timed step receives, as float32 .npy files.
+
+    loss.npy            [1]  the loss the last timed step returned
+    params_sample.npy   [n]  up to DUMP_PER_PARAM elements of every parameter this rank holds whole
+                             after that step, in named_parameters() order.  The element indices come
+                             from a CPU generator seeded with DUMP_SEED, so they depend only on the
+                             parameter shapes.  Parameters ZeRO-3 has released to their shards (N >= 2)
+                             are empty on the module and are left out
+    The caller synchronises the device first (the overlapped optimizer step runs on a side stream)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    g = torch.Generator(device="cpu")
+    g.manual_seed(DUMP_SEED)
+    parts = []
+    for _, p in module.named_parameters():
+        flat = p.detach().reshape(-1)
+        n = flat.numel()
+        if n == 0:
+            continue
+        idx = torch.arange(n) if n <= DUMP_PER_PARAM else torch.randint(0, n, (DUMP_PER_PARAM,), generator=g)
+        parts.append(flat[idx.to(flat.device)].float().cpu())
+    sample = torch.cat(parts) if parts else torch.zeros(0)
+    np.save(os.path.join(path, "params_sample.npy"), sample.numpy())
+    log(f"outputs of the last timed step written to {path}: loss.npy, params_sample.npy "
+        f"({sample.numel()} elements of {len(parts)} tensors)")
 
 
 def plan_memory(cfg, mb, seq, world, offload, ckpt, ga=1):
@@ -837,6 +885,8 @@ def main():
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, engine.module)
 
     if args.profile_steps > 0:
         from torch.profiler import ProfilerActivity, profile
@@ -1085,6 +1135,8 @@ def run_pipeline(args, cfg, mb, ga, world, rank, dev, hb):
     t = torch.tensor([time.time() - t_start], device=dev, dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch.as_tensor(loss), engine.module)
     timed_losses = [round(float(l), 4) for l in timed_losses]
     global_batch = mb * ga * dp
     tps = global_batch * args.seq * args.steps / elapsed

@@ -44,6 +44,33 @@ def test_bench_zero2_label():
     assert out["metric"].startswith("tokens/sec tiny ZeRO-2")
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's loss and parameter sample as float32 .npy
+    files; the same arguments give the same seeded weights and batches, so two runs write the same
+    arrays.  `--full` is accepted and `--steps` is the number of timed steps the record reports."""
+    import numpy as np
+    outs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = _run(["--gpus", "1", "--model", "tiny", "--seq", "64", "--steps", "3", "--warmup", "1",
+                  "--dump-outputs", str(d)] + extra,
+                 extra_env={"WORLD_SIZE": "1", "HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"})  # CPU run
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        rec = json.loads(r.stdout.decode().strip())
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert "[hb] rank=0 timed step 2 queued" in r.stderr.decode()
+        assert "timed step 3 queued" not in r.stderr.decode()
+        assert sorted(p.name for p in d.iterdir()) == ["loss.npy", "params_sample.npy"]
+        arrs = {p.name: np.load(p) for p in d.iterdir()}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        assert arrs["loss.npy"].shape == (1,) and arrs["params_sample.npy"].size > 0
+        assert abs(float(arrs["loss.npy"][0]) - rec["config"]["final_loss"]) <= 1e-3
+        outs.append(arrs)
+    for k in outs[0]:
+        np.testing.assert_array_equal(outs[0][k], outs[1][k])
+
+
 def test_bench_rank_failure_stops_all():
     r = _run(["--gpus", "2", "--model", "tiny", "--seq", "64", "--steps", "2", "--warmup", "1"],
              extra_env={"DSA_BENCH_FAIL_RANK": "1"}, timeout=120)

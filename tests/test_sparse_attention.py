@@ -3,25 +3,25 @@ the reference's pure-Python configs, MatMul sdd/dsd/dds (all transpositions) and
 rpe, masks) vs dense PyTorch, gradients, and SparseSelfAttention == dense attention on a dense
 layout.  CPU here; the HIP kernels are compared against these in test_kernels_gpu.py."""
 
-import importlib.util
 import os
 import random
 
+import numpy as np
 import pytest
 import torch
 
 import deeperspeed_amd.ops.sparse_attention as sa
 
-REF = "/root/reference/deepspeed/ops/sparse_attention/sparsity_config.py"
+# Layouts recorded from the reference's sparsity_config.py (its `make_layout(seq)` after
+# `random.seed(1234)`), one uint8 [heads, blocks, blocks] array per (case, seq), keyed
+# "case<index in CASES>_<config class>_seq<seq>".  A new case needs its layout recorded there.
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sparsity_layouts.npz")
 
 
-def _ref_module():
-    if not os.path.exists(REF):
-        pytest.skip("reference sources not mounted")
-    spec = importlib.util.spec_from_file_location("ref_sparsity_config", REF)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)  # plain torch + random, no native code
-    return mod
+@pytest.fixture(scope="module")
+def ref_layouts():
+    with np.load(GOLDEN) as z:
+        return {k: torch.from_numpy(z[k]).long() for k in z.files}
 
 
 CASES = [
@@ -47,10 +47,8 @@ CASES = [
 
 @pytest.mark.parametrize("name,kw", CASES)
 @pytest.mark.parametrize("seq", [256, 336])
-def test_layouts_match_reference(name, kw, seq):
-    ref = _ref_module()
-    random.seed(1234)
-    a = getattr(ref, name)(**kw).make_layout(seq)
+def test_layouts_match_reference(name, kw, seq, ref_layouts):
+    a = ref_layouts[f"case{CASES.index((name, kw)):02d}_{name}_seq{seq}"]  # int64, as the reference returns it
     random.seed(1234)
     b = getattr(sa, name)(**kw).make_layout(seq)
     assert torch.equal(a, b)
